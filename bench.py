@@ -11,7 +11,9 @@ darknet_dynamic.cfg + reweighting_net.cfg, fp32, train step, 1 MI355X.  BASELINE
 (15 base classes, supports at the cfg's 416x416) is timed in the same run and reported under `also_measured`
 (`--classes 15 --support 416` makes it the headline line instead).
 
-    python bench.py --gpus 1 --steps 10 --warmup 3
+    python bench.py --gpus 1 --steps 10 --warmup 3                  # the headline: set-up, warm-up, timed steps, one line
+    python bench.py --gpus 1 --steps 10 --warmup 3 --full           # + also_measured, CPU baseline, parity vs the oracle
+    python bench.py --gpus 1 --steps 10 --warmup 3 --dump-outputs D # + what the last timed step computed, as D/<name>.npy
     python -m torch.distributed.run --nnodes=1 --nproc-per-node 8 --master-addr 127.0.0.1 \
            --master-port 29500 bench.py --gpus 8 --steps 10 --warmup 3 [--scaling strong]
 
@@ -210,7 +212,9 @@ def cpu_baseline_and_parity(dyn_cfg, rw_cfg, args, full_flops, dev, dtypes, worl
     from oracle.net import OracleDarknet
     from oracle.region import region_loss_v2
     from fewshot_detection_amd.cfg import parse_cfg
-    cores = min(os.cpu_count() or 1, 64)
+    # the cores this process may use: OMP_NUM_THREADS where it is set, else the CPU affinity (os.cpu_count() is the whole host's)
+    cores = int(os.environ.get("OMP_NUM_THREADS", "0") or 0) or len(os.sched_getaffinity(0)) or 1
+    cores = min(cores, 64)
     torch.set_num_threads(cores)
     Bs, Ns = (args.batch if cores >= 32 else min(args.batch, 32)), args.classes
     torch.manual_seed(4242)
@@ -333,6 +337,8 @@ class Leg(object):
         self.region = self.net.models[len(self.net.models) - 1]
         self.region.verbose = False
         self.opt = None
+        # --dump-outputs: the same number of untimed steps in every run (Leg.run) and the last timed step's network output kept
+        self.dump, self.keep_out, self.last_out = False, False, None
         from fewshot_detection_amd import streams as _streams
         self.streams_requested = bool(_streams.ENABLED)     # the process-wide request (flag / environment), the same on every rank
         if mode == "train":
@@ -352,7 +358,11 @@ class Leg(object):
 
         def step():
             region.seen += gb
-            loss = region(net(x, metax, mask), target)
+            out = net(x, metax, mask)
+            if self.keep_out:
+                self.last_out = out.detach()
+            loss = region(out, target)
+            del out                           # (not held through the backward pass)
             if opt is not None:
                 opt.backward_and_step(loss)
             return loss.detach()              # (a loss that is kept must not keep the step's autograd graph alive)
@@ -383,7 +393,7 @@ class Leg(object):
             # mapping makes a step 40 % slower for the life of the streams; it re-draws them or falls back to one stream)
             # (several ranks: a FIXED number of probing steps on every rank -- each step holds the gradient collectives --
             # whatever a rank decided in an earlier leg: the condition must be the same on every rank)
-            self.stream_tuning = streams.autotune(step, fixed_schedule=self.dist is not None)
+            self.stream_tuning = streams.autotune(step, fixed_schedule=self.dist is not None or self.dump)
             streams_on = streams.ENABLED
             self.fence()
         # untimed: let the caching allocator reach its steady state (tensors that cross streams are re-used only after the
@@ -429,7 +439,7 @@ class Leg(object):
                     q = torch.tensor([1 if quiet else 0], dtype=torch.int32, device=self.dev)
                     self.dist.all_reduce(q, op=self.dist.ReduceOp.MIN)
                     quiet = bool(int(q.item()))
-                if quiet:
+                if quiet and not self.dump:
                     break
             self.fence()
         if self.opt is not None:
@@ -455,8 +465,10 @@ class Leg(object):
                 ops.PROFILE = None
                 ops.kernel_profile(False)
                 streams.ENABLED = streams_on
+            self.keep_out = self.dump and i == steps - 1
             loss = step()
             step_ev[i + 1].record()
+        self.keep_out = False
         ops.PROFILE = None
         ops.kernel_profile(False)
         streams.ENABLED = streams_on
@@ -769,6 +781,37 @@ def emit(res, out_dir=None, stream=None):
     return line
 
 
+DUMP_OUTPUT_ELEMS = 1 << 23       # --dump-outputs: the network output whole up to 32 MB, else a seeded sample of this many
+DUMP_PARAM_ELEMS = 1 << 21        # ... and a seeded sample of the flat weights / gradient buffers (8 MB each)
+
+
+def _sample(t, k, seed):
+    """`t` flattened if it has at most `k` elements, else `k` elements at fixed, seeded positions (ascending)."""
+    t = t.detach().reshape(-1)
+    if t.numel() <= k:
+        return t
+    idx = torch.randint(0, t.numel(), (k,), generator=torch.Generator().manual_seed(seed)).sort().values
+    return t[idx.to(t.device)]
+
+
+def dump_outputs(leg, loss, out_dir):
+    """--dump-outputs: what the last timed step computed, as its caller receives it -- the loss, the network output and, in
+    train mode, the weights after the optimizer step and the step's gradient (flat buffers of the trainer) -> DIR/<name>.npy."""
+    os.makedirs(out_dir, exist_ok=True)
+    out = leg.last_out
+    arrays = {"loss": np.array([loss], np.float64)}
+    if out.numel() <= DUMP_OUTPUT_ELEMS:
+        arrays["output"] = out.float().cpu().numpy()
+    else:
+        arrays["output_sample"] = _sample(out, DUMP_OUTPUT_ELEMS, 1).float().cpu().numpy()
+    if leg.opt is not None:
+        arrays["weights_sample"] = _sample(leg.opt.flat, DUMP_PARAM_ELEMS, 0).float().cpu().numpy()
+        arrays["grad_sample"] = _sample(leg.opt.grad, DUMP_PARAM_ELEMS, 0).float().cpu().numpy()
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+    return {k: list(a.shape) for k, a in arrays.items()}
+
+
 def backbone_forward(dyn_cfg, dtype, dev, B, S):
     """north_star's literal target: the Darknet-19 backbone (layers 0-22 of darknet_dynamic.cfg, 18.906 GFLOP / image,
     BASELINE.md) forward at B=64, 416x416 on one MI355X, as the training forward runs it (train-mode BatchNorm from the
@@ -950,15 +993,26 @@ def main():
                                                             "tail is split 5.7 / 1 / 0.3 percent of the buffer: measured no faster)")
     ap.add_argument("--no-settle", action="store_true", help="profiling aid: skip the untimed allocator-settle steps (rocprofv3 "
                                                              "PMC passes replay every kernel several times)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-parity", action="store_true", help="skip the HIP-vs-oracle comparison on the cpu_baseline sample")
-    ap.add_argument("--no-extras", action="store_true", help="skip also_measured (bf16 mode, backbone forward, other configs, ...)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check everything beyond the headline: also_measured (sustained run, bf16 mode, "
+                         "backbone forward, other configs, inference, the other fp32 GEMM arithmetic, the other scaling form), "
+                         "the CPU baseline and the HIP-vs-oracle parity.  A plain run sets up, warms up, times --steps steps and "
+                         "prints the line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step computed to DIR/<name>.npy (float32 / float64; "
+                         "the untimed steps before the timed region follow a fixed schedule, so the same arguments give the "
+                         "same inputs to that step in every run)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baseline (and its parity check)")
+    ap.add_argument("--no-parity", action="store_true", help="--full without the HIP-vs-oracle comparison on the cpu_baseline sample")
+    ap.add_argument("--no-extras", action="store_true", help="--full without also_measured (bf16 mode, backbone forward, other configs, ...)")
     ap.add_argument("--per-layer", action="store_true", help="print per-launch conv timing to stderr")
     ap.add_argument("--f32-gemm", choices=["split", "native"], default=None,
                     help="arithmetic of the fp32 GEMM kernels: split = six bf16 MFMA terms of three-way split fp32 operands, fp32 "
                          "accumulate (default; error <= the native instruction's, tests/test_gpu_split.py); native = "
                          "v_mfma_f32_32x32x2_f32.  The default line also times the native arithmetic (also_measured)")
     args = ap.parse_args()
+    if not args.full:                      # a plain run: the headline and nothing else
+        args.no_extras = args.no_cpu_baseline = args.no_parity = True
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         raise SystemExit(self_launch(args.gpus))
     try:                                   # the boxes are shared: ask the scheduler for the host cores the ~460 launches per
@@ -1026,6 +1080,7 @@ def _main(args, real_stdout):
     leg = Leg(dyn_cfg, rw_cfg, args.dtype, dev, dist, global_batch, args.mode, single_rank_collectives=single_rank,
               n_buckets=args.buckets)
     leg.no_settle = args.no_settle
+    leg.dump = bool(args.dump_outputs)
     if strong:      # one global episode: this rank's slice of the queries and targets, every support on every rank
         gx, metax, mask, gt = synth_episode(1000, args.batch, args.classes, args.size, args.support)
         x, target = gx[rank * local_batch:(rank + 1) * local_batch], gt[rank * local_batch:(rank + 1) * local_batch]
@@ -1037,9 +1092,10 @@ def _main(args, real_stdout):
     # The shader clock the chip sustains under matrix-core load (a dependent-MFMA chain, ~1 ms).  A box that was throttled
     # by an earlier tenant / process shows up here as a fraction of the nominal 2400 MHz: wait (bounded) for it to recover
     # instead of timing a throttled GPU, and say so in the line.
+    # (a plain run waits at most 10 s: its whole time outside the timed steps is kept short)
     clock = {"nominal_mhz": 2400.0, "probe_mhz_start": ops.clock_probe_mhz(dev), "waited_s": 0.0}
     t_wait = time.perf_counter()
-    while clock["probe_mhz_start"] < 0.6 * 2400.0 and time.perf_counter() - t_wait < 30.0:
+    while clock["probe_mhz_start"] < 0.6 * 2400.0 and time.perf_counter() - t_wait < (30.0 if args.full else 10.0):
         time.sleep(3.0)
         clock["probe_mhz_start"] = ops.clock_probe_mhz(dev)
         clock["waited_s"] = time.perf_counter() - t_wait
@@ -1047,6 +1103,11 @@ def _main(args, real_stdout):
     clock["probe_mhz_after_timing"] = ops.clock_probe_mhz(dev)
     clock["throttled"] = bool(clock["probe_mhz_after_timing"] < 0.6 * 2400.0)
     elapsed = r["elapsed"]
+    dumped = None
+    if args.dump_outputs:                  # before anything else runs a step on these weights
+        if rank == 0:
+            dumped = dump_outputs(leg, r["loss"], args.dump_outputs)
+        leg.dump, leg.last_out = False, None
 
     # several ranks: the OTHER scaling form on the same replicas (SURVEY 8e asks for both curves; one driver call per N
     # then yields both points).  Every rank runs it -- the steps hold the gradient all-reduce.
@@ -1137,6 +1198,8 @@ def _main(args, real_stdout):
                         "profiled_steps_on_one_stream": r["prof_steps"], "profiled_step_index": r["prof_index"],
                         "ms_per_step_unprofiled": r["ms_unprofiled"], "ms_per_step_profiled": r["ms_profiled"]},
         }
+        if dumped is not None:
+            res["dumped_outputs"] = {"dir": args.dump_outputs, "shapes": dumped}
         if leg.opt is not None:
             o = leg.opt
             res["dp"] = {"world_size": o.world_size, "backend": backend if (world > 1 or single_rank) else None,

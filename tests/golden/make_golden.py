@@ -24,8 +24,13 @@ Outputs (committed, small):
     region_fns.npz       region_loss.build_targets called directly on decoded boxes; region_loss.neg_filter with seeded RNG
     drivers.npz          (drivers_golden.py) the loop body of train_meta.py:201-226 and valid_ensemble.valid() run from the
                          reference's own source on a synthetic tmp dataset
+    live_checks.json / live_checks.npz   what the reference tree itself answers to the checks that once read it directly:
+                         its cfg files parsed, the full-size model's state_dict layout, cfg.config_data, the public names of
+                         its hot-path modules and the names its two drivers use, image.fill_truth_detection_meta on label
+                         files, GlobalMaxPool2d / GlobalAvgPool2d, and RegionLossV2 on the randomised sweep of
+                         tests/test_oracle_vs_reference.py
 
-`python make_golden.py NAME...` regenerates only the named fixtures (decode_valid, ensemble, augment, utils_host, region_fns, drivers); no argument = all.
+`python make_golden.py NAME...` regenerates only the named fixtures (decode_valid, ensemble, augment, utils_host, region_fns, drivers, live_checks); no argument = all.
 
 The GPU box has no /root/reference; tests there read only these files.
 """
@@ -521,6 +526,134 @@ def gold_utils_host(u):
     np.savez_compressed(os.path.join(HERE, "utils_host.npz"), **out)
 
 
+STANDARD_CFGS = ("darknet_dynamic.cfg", "reweighting_net.cfg", "tiny-yolo-voc.cfg")
+PARSED_CFGS = STANDARD_CFGS + ("yolo-voc.cfg",)
+DRIVERS = ("train_meta.py", "valid_ensemble.py")
+DRIVER_OBJS = ("model", "cur_model", "m", "region_loss", "cfg")       # names the drivers read attributes of
+CFG_DATA_OPT = {"metayolo": "1", "metain_type": "2", "data": "voc", "neg": "1", "rand": "0", "novel": "bird,bus,cow",
+                "novelid": "0", "meta": "x", "backup": "backup/metayolo", "gpus": "1,2"}
+CFG_DATA_KEYS = ("neg_ratio", "num_gpus", "base_classes", "base_ids", "novel_ids", "backup", "metayolo", "tuning")
+_LIVE = {}
+
+
+def live_checks():
+    """(live_checks.json as a dict, live_checks.npz) -- loaded once."""
+    if not _LIVE:
+        import json
+        with open(os.path.join(HERE, "live_checks.json")) as fh:
+            _LIVE["json"] = json.load(fh)
+        _LIVE["npz"] = dict(np.load(os.path.join(HERE, "live_checks.npz")))
+    return _LIVE["json"], _LIVE["npz"]
+
+
+def write_cfg_blocks(blocks, path):
+    """Parsed cfg blocks -> cfg text that parses back to them (the parser's own default batch_normalize = 0 is left out)."""
+    with open(path, "w") as fh:
+        for b in blocks:
+            fh.write("[%s]\n" % b["type"])
+            for k, v in b.items():
+                if k == "type" or (k == "batch_normalize" and v == 0 and not isinstance(v, str)):
+                    continue
+                fh.write("%s=%s\n" % ("type" if k == "_type" else k, v))
+            fh.write("\n")
+    return path
+
+
+def public_names(path):
+    """Top-level functions, classes and plain assignments of a python-2 era source file (parsed, not imported)."""
+    import ast
+    tree = ast.parse(open(path).read())
+    names, methods = [], {}
+    for node in tree.body:
+        if isinstance(node, (ast.FunctionDef, ast.ClassDef)):
+            names.append(node.name)
+            if isinstance(node, ast.ClassDef):
+                methods[node.name] = [b.name for b in node.body if isinstance(b, ast.FunctionDef)]
+        elif isinstance(node, ast.Assign):
+            names += [t.id for t in node.targets if isinstance(t, ast.Name)]
+    return names, methods
+
+
+def driver_uses(path, utils_names):
+    """(attributes a driver reads from DRIVER_OBJS as [obj, attr] pairs, bare calls of functions named in `utils_names`)."""
+    import ast
+    attrs, calls = [], []
+    for node in ast.walk(ast.parse(open(path).read())):
+        if isinstance(node, ast.Attribute) and isinstance(node.value, ast.Name) and node.value.id in DRIVER_OBJS:
+            attrs.append([node.value.id, node.attr])
+        if isinstance(node, ast.Call) and isinstance(node.func, ast.Name) and node.func.id in utils_names:
+            calls.append(node.func.id)
+    return attrs, calls
+
+
+def live_episode_cases():
+    """Label rows and augmentation parameters of the six fill_truth_detection_meta cases (base ids 1, 4, 6 of 8 classes)."""
+    rng = np.random.RandomState(3)
+    cases = []
+    for k in range(6):
+        n = int(rng.randint(1, 12))
+        rows = np.column_stack([rng.randint(0, 8, n), rng.uniform(0, 1, (n, 2)), rng.uniform(0.0, 0.5, (n, 2))])
+        flip, (dx, dy), (sx, sy) = int(k % 2), rng.uniform(-0.2, 0.2, 2), rng.uniform(0.8, 1.25, 2)
+        cases.append((rows, (flip, dx, dy, sx, sy)))
+    return cases
+
+
+def gold_live_checks():
+    import json
+    import tempfile
+    sys.path[:0] = [os.path.dirname(HERE), os.path.dirname(os.path.dirname(HERE))]     # tests/, the repository
+    from fewshot_detection_amd.cfg import parse_cfg as fsd_parse_cfg
+    import test_oracle_vs_reference as tovr
+    cfgdir = os.path.join(ref_shim.REF, "cfg")
+    cfgmod = ref_shim.load("cfg")
+    js, arr = {}, {}
+    # cfg files: the project's parser on them (normalised as tests/test_cfgs.py compares) and the reference's own parser
+    js["cfg_blocks"] = {n: [{k: str(v).replace(" ", "") for k, v in b.items()} for b in fsd_parse_cfg(os.path.join(cfgdir, n))]
+                        for n in STANDARD_CFGS}
+    js["reference_parse_cfg"] = {n: cfgmod.parse_cfg(os.path.join(cfgdir, n)) for n in PARSED_CFGS}
+    dm = ref_shim.load("darknet_meta")
+    sd = dm.Darknet(os.path.join(cfgdir, "darknet_dynamic.cfg"), os.path.join(cfgdir, "reweighting_net.cfg")).state_dict()
+    js["state_dict_shapes"] = [[k, list(v.shape)] for k, v in sd.items()]
+    ref = cfgmod.cfg
+    ref.config_data(dict(CFG_DATA_OPT))
+    js["cfg_data"] = {k: ref[k] for k in CFG_DATA_KEYS}
+    js["public_names"] = {m: public_names(os.path.join(ref_shim.REF, m + ".py"))
+                          for m in ("utils", "cfg", "darknet_meta", "darknet", "region_loss", "dynamic_conv", "pooling")}
+    utils_names = js["public_names"]["utils"][0]
+    js["driver_uses"] = {d: driver_uses(os.path.join(ref_shim.REF, d), utils_names) for d in DRIVERS}
+    # image.fill_truth_detection_meta on label files
+    im = ref_shim.load("image")
+    im.cfg.base_ids, im.cfg.base_classes, im.cfg.yolo_joint, im.cfg.metaids = [1, 4, 6], ["a", "b", "c"], False, []
+    tmp = tempfile.mkdtemp()
+    for k, (rows, (flip, dx, dy, sx, sy)) in enumerate(live_episode_cases()):
+        path = os.path.join(tmp, "%d.txt" % k)
+        np.savetxt(path, rows, fmt="%.17g")
+        arr["episode%d" % k] = im.fill_truth_detection_meta(path, 9, 9, flip, dx, dy, sx, sy)
+    pl = ref_shim.load("pooling")
+    x = torch.randn(3, 16, 6, 6, generator=torch.Generator().manual_seed(3))
+    arr["pool_max"], arr["pool_avg"] = pl.GlobalMaxPool2d()(x).numpy(), pl.GlobalAvgPool2d()(x).numpy()
+    # RegionLossV2 on the sweep's inputs
+    rl = ref_shim.load("region_loss")
+    for seed in range(16):
+        out, tgt, seen, neg, skip = tovr._sweep_case(seed)
+        if skip:
+            continue
+        mod = rl.RegionLossV2()
+        mod.anchors, mod.num_anchors, mod.num_classes, mod.anchor_step = ANCH, 5, 1, 2
+        mod.seen = seen
+        cfgmod.cfg.neg_ratio = neg
+        try:
+            random.seed(seed)
+            res = _run_loss(rl, mod, out, torch.from_numpy(tgt))
+        finally:
+            cfgmod.cfg.neg_ratio = "full"
+        for k, v in res.items():
+            arr["sweep%d_%s" % (seed, k)] = np.asarray(v)
+    with open(os.path.join(HERE, "live_checks.json"), "w") as fh:
+        json.dump(js, fh, indent=0, sort_keys=True)
+    np.savez_compressed(os.path.join(HERE, "live_checks.npz"), **arr)
+
+
 def main():
     assert ref_shim.available(), "needs /root/reference"
     only = set(sys.argv[1:])
@@ -539,6 +672,8 @@ def main():
         if "drivers" in only:
             import drivers_golden
             drivers_golden.mint()
+        if "live_checks" in only:
+            gold_live_checks()
         print("golden vectors written to", HERE, sorted(only))
         return
     u = ref_shim.load("utils")

@@ -1,4 +1,5 @@
-"""Generated cfg text == the reference's cfg files, block by block (needs /root/reference; CPU only)."""
+"""Generated cfg text == the reference's cfg files, block by block (their parsed blocks: tests/golden/live_checks.json,
+minted by tests/golden/make_golden.py; CPU only)."""
 import os
 import sys
 
@@ -8,19 +9,19 @@ from fewshot_detection_amd import cfgs
 from fewshot_detection_amd.cfg import parse_cfg
 
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden"))
-import ref_shim  # noqa: E402
+import make_golden  # noqa: E402
 
 
 def _norm(blocks):
     return [{k: str(v).replace(" ", "") for k, v in b.items()} for b in blocks]
 
 
-@pytest.mark.skipif(not ref_shim.available(), reason="/root/reference not present")
 def test_generated_cfgs_equal_reference_files(tmp_path):
     dyn, rw, tiny = cfgs.write_standard_cfgs(str(tmp_path))
+    gold = make_golden.live_checks()[0]["cfg_blocks"]
     for mine, ref in ((dyn, "darknet_dynamic.cfg"), (rw, "reweighting_net.cfg"), (tiny, "tiny-yolo-voc.cfg")):
         a = _norm(parse_cfg(mine))
-        b = _norm(parse_cfg(os.path.join(ref_shim.REF, "cfg", ref)))
+        b = gold[ref]
         assert len(a) == len(b), ref
         for i, (x, y) in enumerate(zip(a, b)):
             assert x == y, (ref, i, x, y)

@@ -2,7 +2,6 @@
 of the reference tree on PYTHONPATH, every public name of the reference's hot-path modules resolves here, the
 reference's own dataset.py imports, and the host helpers of utils.py return what the reference's return
 (tests/golden/utils_host.npz, region_fns.npz -- minted from the reference's source by tests/golden/make_golden.py)."""
-import ast
 import os
 import random
 import subprocess
@@ -22,29 +21,13 @@ import ref_shim  # noqa: E402
 HOT_MODULES = ("utils", "cfg", "darknet_meta", "darknet", "region_loss", "dynamic_conv", "pooling")
 
 
-def _public_names(path):
-    """Top-level functions, classes and plain assignments of a python-2 era source file (parsed, not imported)."""
-    tree = ast.parse(open(path).read())
-    names, methods = [], {}
-    for node in tree.body:
-        if isinstance(node, (ast.FunctionDef, ast.ClassDef)):
-            names.append(node.name)
-            if isinstance(node, ast.ClassDef):
-                methods[node.name] = [b.name for b in node.body if isinstance(b, ast.FunctionDef)]
-        elif isinstance(node, ast.Assign):
-            names += [t.id for t in node.targets if isinstance(t, ast.Name)]
-    return names, methods
-
-
-@pytest.mark.skipif(not ref_shim.available(), reason="/root/reference not present")
 def test_every_public_name_of_the_reference_modules_resolves_under_the_integration_recipe():
     """INTEGRATION.md §1 verbatim: PYTHONPATH = repo : repo/fewshot_detection_amd/compat : reference.  The name lists
-    are derived from the reference files with `ast`; dataset.py / image.py are the REFERENCE's own files and must import
-    against the compat modules (torchvision is not installed in this image: a two-class stand-in is injected)."""
-    want = {}
-    for mod in HOT_MODULES:
-        names, methods = _public_names(os.path.join(ref_shim.REF, mod + ".py"))
-        want[mod] = (names, methods)
+    are derived from the reference files with `ast` (tests/golden/live_checks.json, make_golden.py); where the reference tree
+    is on the path, its own dataset.py / image.py must import against the compat modules as well (torchvision is not
+    installed in this image: a two-class stand-in is injected)."""
+    import make_golden
+    want = {mod: make_golden.live_checks()[0]["public_names"][mod] for mod in HOT_MODULES}
     script = textwrap.dedent("""
         import importlib, json, sys, types
         try:
@@ -72,20 +55,23 @@ def test_every_public_name_of_the_reference_modules_resolves_under_the_integrati
             for cls, ms in methods.items():
                 if hasattr(m, cls):
                     missing += ["%s.%s.%s" % (mod, cls, x) for x in ms if not hasattr(getattr(m, cls), x)]
-        import dataset, image                                    # the reference's own files
-        assert "fewshot_detection_amd" not in dataset.__file__
+        if sys.argv[2] == "1":
+            import dataset, image                                # the reference's own files
+            assert "fewshot_detection_amd" not in dataset.__file__
+            assert dataset.read_truths_args.__module__.startswith("fewshot_detection_amd")
         ns = {}
         exec("from utils import *", ns)
         for n in ("read_data_cfg", "get_region_boxes_v2", "nms", "get_image_size", "bbox_iou", "logging", "file_lines"):
             assert n in ns, n
         from darknet_meta import Darknet                         # noqa
         from cfg import parse_cfg, cfg                           # noqa
-        assert dataset.read_truths_args.__module__.startswith("fewshot_detection_amd")
         print(json.dumps(missing))
     """)
     import json
-    env = dict(os.environ, PYTHONPATH=os.pathsep.join([ROOT, COMPAT, ref_shim.REF]))
-    out = subprocess.run([sys.executable, "-c", script, json.dumps(want)], env=env, capture_output=True, text=True,
+    have_ref = ref_shim.available()
+    env = dict(os.environ, PYTHONPATH=os.pathsep.join([ROOT, COMPAT] + ([ref_shim.REF] if have_ref else [])))
+    out = subprocess.run([sys.executable, "-c", script, json.dumps(want), "1" if have_ref else "0"], env=env,
+                         capture_output=True, text=True,
                          cwd=str(ROOT), timeout=600)
     assert out.returncode == 0, out.stderr[-3000:]
     missing = json.loads(out.stdout.strip().splitlines()[-1])
@@ -190,27 +176,28 @@ def test_neg_filter_function_matches_the_reference():
         cfg.neg_ratio = saved
 
 
-@pytest.mark.skipif(not ref_shim.available(), reason="/root/reference not present")
 def test_reference_drivers_only_use_names_the_boundary_has():
     """Static cross-check of the two drivers the north star names: every attribute they read from the model / loss /
-    cfg objects and every bare function they call from `utils` exists on this side (train_meta.py, valid_ensemble.py)."""
+    cfg objects and every bare function they call from `utils` exists on this side (train_meta.py, valid_ensemble.py;
+    what they use: tests/golden/live_checks.json, collected with `ast` by make_golden.py)."""
+    import make_golden
     from fewshot_detection_amd import cfg as cfgmod
     from fewshot_detection_amd import utils as u
     from fewshot_detection_amd.darknet_meta import Darknet
     from fewshot_detection_amd.region_loss import RegionLossV2
     net = Darknet(os.path.join(GOLD, "mini_dynamic.cfg"), os.path.join(GOLD, "mini_reweight.cfg"))
-    ref_utils_names, _ = _public_names(os.path.join(ref_shim.REF, "utils.py"))
+    uses = make_golden.live_checks()[0]["driver_uses"]
     objs = {"model": net, "cur_model": net, "m": net, "region_loss": RegionLossV2(), "cfg": cfgmod.cfg}
+    assert sorted(objs) == sorted(make_golden.DRIVER_OBJS) and sorted(uses) == sorted(make_golden.DRIVERS)
     cfg_keys_set_later = {"backup", "base_classes", "classes", "data", "novel_classes", "num_gpus", "batch_size", "max_epoch",
                           "novelid", "_real_base_ids", "tuning", "repeat", "save_interval", "neg_ratio"}
-    for drv in ("train_meta.py", "valid_ensemble.py"):
-        tree = ast.parse(open(os.path.join(ref_shim.REF, drv)).read())
-        for node in ast.walk(tree):
-            if isinstance(node, ast.Attribute) and isinstance(node.value, ast.Name) and node.value.id in objs:
-                if node.value.id == "cfg" and node.attr in cfg_keys_set_later:
-                    continue
-                if node.attr == "module":                      # nn.DataParallel wrapper, replaced by one process per GPU
-                    continue
-                assert hasattr(objs[node.value.id], node.attr), (drv, node.value.id, node.attr)
-            if isinstance(node, ast.Call) and isinstance(node.func, ast.Name) and node.func.id in ref_utils_names:
-                assert hasattr(u, node.func.id), (drv, node.func.id)
+    for drv, (attrs, calls) in uses.items():
+        assert attrs and calls, drv
+        for obj, attr in attrs:
+            if obj == "cfg" and attr in cfg_keys_set_later:
+                continue
+            if attr == "module":                                # nn.DataParallel wrapper, replaced by one process per GPU
+                continue
+            assert hasattr(objs[obj], attr), (drv, obj, attr)
+        for fn in calls:
+            assert hasattr(u, fn), (drv, fn)

@@ -1,5 +1,5 @@
 """Host-side episode bookkeeping (fewshot_detection_amd/episode.py) against fixtures minted from the reference's own
-functions (tests/golden/make_golden.py: gold_episode) and, when /root/reference is present, against the live reference."""
+functions (tests/golden/make_golden.py: gold_episode, gold_live_checks)."""
 import os
 import sys
 
@@ -50,26 +50,17 @@ def test_missing_label_file_and_keep_all():
     assert np.allclose(kept[:5], [7, 0.5, 0.5, 0.2, 0.2])
 
 
-def test_live_reference_agrees():
-    import ref_shim
-    if not ref_shim.available():
-        pytest.skip("reference tree not present")
+def test_live_reference_agrees(tmp_path):
+    """fill_truth_detection_meta on label files == the reference's image.fill_truth_detection_meta (base ids 1, 4, 6; its
+    results: tests/golden/live_checks.npz)."""
+    import make_golden
     from fewshot_detection_amd import episode
-    ref_shim.load("cfg")
-    im = ref_shim.load("image")
-    base_ids = [1, 4, 6]
-    im.cfg.base_ids, im.cfg.base_classes, im.cfg.yolo_joint, im.cfg.metaids = base_ids, ["a", "b", "c"], False, []
-    rng = np.random.RandomState(3)
-    import tempfile
-    tmp = tempfile.mkdtemp()
-    for k in range(6):
-        n = int(rng.randint(1, 12))
-        rows = np.column_stack([rng.randint(0, 8, n), rng.uniform(0, 1, (n, 2)), rng.uniform(0.0, 0.5, (n, 2))])
-        path = os.path.join(tmp, "%d.txt" % k)
+    ref = make_golden.live_checks()[1]
+    for k, (rows, (flip, dx, dy, sx, sy)) in enumerate(make_golden.live_episode_cases()):
+        path = os.path.join(str(tmp_path), "%d.txt" % k)
         np.savetxt(path, rows, fmt="%.17g")
-        flip, (dx, dy), (sx, sy) = int(k % 2), rng.uniform(-0.2, 0.2, 2), rng.uniform(0.8, 1.25, 2)
-        assert np.array_equal(im.fill_truth_detection_meta(path, 9, 9, flip, dx, dy, sx, sy),
-                              episode.fill_truth_detection_meta(path, 9, 9, flip, dx, dy, sx, sy, base_ids=base_ids, n_cls=3,
+        assert np.array_equal(ref["episode%d" % k],
+                              episode.fill_truth_detection_meta(path, 9, 9, flip, dx, dy, sx, sy, base_ids=[1, 4, 6], n_cls=3,
                                                                 max_boxes=50))
 
 

@@ -108,7 +108,7 @@ def test_bench_two_ranks_one_json_line():
     for attempt in range(2):            # the rendezvous port is picked, released and re-bound by torchrun: allow one retry
         cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr",
                "127.0.0.1", "--master-port", str(_free_port()), os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps",
-               "2", "--warmup", "1", "--batch", "4", "--classes", "3", "--size", "160", "--support", "160"]
+               "2", "--warmup", "1", "--batch", "4", "--classes", "3", "--size", "160", "--support", "160", "--full"]
         out = subprocess.run(cmd, env=env, cwd=ROOT, capture_output=True, text=True, timeout=600)
         if out.returncode == 0:
             break
@@ -136,7 +136,7 @@ def test_plain_bench_command_launches_its_own_ranks():
     for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT"):
         env.pop(k, None)
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--batch", "4",
-           "--classes", "3", "--size", "160", "--support", "160"]
+           "--classes", "3", "--size", "160", "--support", "160", "--full"]
     out = subprocess.run(cmd, env=env, cwd=ROOT, capture_output=True, text=True, timeout=900)
     assert out.returncode == 0, out.stderr[-3000:]
     res = json.loads(out.stdout.strip().splitlines()[-1])
@@ -182,7 +182,7 @@ def test_bench_eight_ranks_strong_form_of_the_headline_episode_on_one_gpu():
     # (--no-cpu-baseline: the CPU baseline / in-line parity of a multi-rank line is asserted by the 2-rank test above, and the
     # B = 8 slice against the oracle by tests/test_gpu_launch_configs.py; here they would be 45 s of host time)
     res = _run_bench(["--scaling", "strong", "--batch", "64", "--classes", "20", "--size", "416", "--support", "224",
-                      "--no-cpu-baseline"], {"FSD_BENCH_BACKEND": "gloo"}, nproc=8, timeout=1500)
+                      "--full", "--no-cpu-baseline"], {"FSD_BENCH_BACKEND": "gloo"}, nproc=8, timeout=1500)
     assert res["n_gpus"] == 8 and res["scaling"] == "strong" and res["config"]["global_batch"] == 64
     dp = res["dp"]
     assert dp["world_size"] == 8 and dp["rccl_ranks"] == 8 and dp["gradient_buckets"] == 6

@@ -189,3 +189,31 @@ def test_bench_timed_region_allocates_no_device_memory():
     d = json.loads(out.stdout.strip().splitlines()[-1])
     assert d["steps"] == 12 and d["value"] > 0
     assert d["allocator"]["device_allocs_in_timed_region"] == 0, d["allocator"]
+
+
+def test_bench_dump_outputs_repeat_from_run_to_run(tmp_path):
+    """bench.py --dump-outputs: the last timed step's loss, network output, weights and gradient (seeded samples) as float
+    .npy files under 64 MB, and two runs with the same arguments dump the same values (the untimed steps before the timed
+    region follow a fixed schedule, so the last timed step sees the same weights, optimizer state and inputs)."""
+    import json
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    dumps = []
+    for k in range(2):
+        d = tmp_path / ("run%d" % k)
+        cmd = [sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "2", "--batch", "4",
+               "--classes", "3", "--size", "160", "--support", "160", "--dump-outputs", str(d)]
+        out = subprocess.run(cmd, cwd=root, capture_output=True, text=True, timeout=600)
+        assert out.returncode == 0, out.stderr[-2000:]
+        line = json.loads(out.stdout.strip().splitlines()[-1])
+        assert line["steps"] == 3 and line["ms_per_step"] > 0 and "cpu_baseline" not in line and "also_measured" not in line
+        files = sorted(os.listdir(str(d)))
+        assert files == ["grad_sample.npy", "loss.npy", "output.npy", "weights_sample.npy"], files
+        assert sum(os.path.getsize(str(d / f)) for f in files) < 64 << 20
+        arrs = {f: np.load(str(d / f)) for f in files}
+        assert all(a.dtype in (np.float32, np.float64) and np.isfinite(a).all() for a in arrs.values())
+        assert arrs["output.npy"].shape == (4 * 3, 30, 5, 5)
+        dumps.append(arrs)
+    for f, a in dumps[0].items():
+        assert np.allclose(a, dumps[1][f], rtol=1e-5, atol=1e-6), f

@@ -150,17 +150,15 @@ def test_cfg_data_plumbing(tmp_path):
         cfg.update(saved)
 
 
-@pytest.mark.skipif(not ref_shim.available(), reason="/root/reference not present")
 def test_cfg_data_plumbing_matches_live_reference(tmp_path):
+    """cfg.config_data on the options train_meta.py passes == the reference's (its values: tests/golden/live_checks.json)."""
+    import make_golden
     from fewshot_detection_amd.cfg import cfg
-    ref = ref_shim.load("cfg").cfg
-    opt = {"metayolo": "1", "metain_type": "2", "data": "voc", "neg": "1", "rand": "0", "novel": "bird,bus,cow",
-           "novelid": "0", "meta": "x", "backup": "backup/metayolo", "gpus": "1,2"}
+    ref = make_golden.live_checks()[0]["cfg_data"]
     saved = dict(cfg)
     try:
-        cfg.config_data(dict(opt))
-        ref.config_data(dict(opt))
-        for k in ("neg_ratio", "num_gpus", "base_classes", "base_ids", "novel_ids", "backup", "metayolo", "tuning"):
+        cfg.config_data(dict(make_golden.CFG_DATA_OPT))
+        for k in make_golden.CFG_DATA_KEYS:
             assert cfg[k] == ref[k], k
     finally:
         cfg.clear()

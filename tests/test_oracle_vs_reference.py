@@ -1,5 +1,4 @@
-"""Pin the CPU oracle against golden vectors minted from the reference itself
-(tests/golden/make_golden.py) and, when /root/reference is present, against the live reference.
+"""Pin the CPU oracle against golden vectors minted from the reference itself (tests/golden/make_golden.py).
 CPU only."""
 import os
 import random
@@ -15,11 +14,10 @@ from oracle.net import OracleDarknet, OracleYolo, reweight
 
 GOLD = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
 sys.path.insert(0, GOLD)
-import ref_shim  # noqa: E402
+import make_golden  # noqa: E402
 
 ANCH = [1.3221, 1.73145, 3.19275, 4.00944, 5.05587, 8.09892, 9.47112, 4.84053, 11.2364, 10.0071]
 ANCH_V1 = [1.08, 1.19, 3.42, 4.41, 6.63, 11.38, 9.42, 5.11, 16.62, 10.52]
-needs_ref = pytest.mark.skipif(not ref_shim.available(), reason="/root/reference not present")
 
 
 def test_iou_matches_reference_goldens():
@@ -141,23 +139,29 @@ def test_hand_derived_single_box():
     assert abs(r["parts"][5].item() - 0.0) < 1e-6              # one class -> softmax over N=1 is certain
 
 
-@needs_ref
-def test_parse_cfg_matches_live_reference():
-    ref = ref_shim.load("cfg")
-    for name in ("darknet_dynamic.cfg", "reweighting_net.cfg", "tiny-yolo-voc.cfg", "yolo-voc.cfg"):
-        p = os.path.join(ref_shim.REF, "cfg", name)
-        assert parse_cfg(p) == ref.parse_cfg(p)
+def test_parse_cfg_matches_live_reference(tmp_path):
+    """The oracle's cfg parser == the reference's parse_cfg on the reference's cfg files (its results:
+    tests/golden/live_checks.json).  The three standard files are the ones fewshot_detection_amd.cfgs writes (equal to the
+    reference's, tests/test_cfgs.py); yolo-voc.cfg is written back from the parsed blocks."""
+    from fewshot_detection_amd import cfgs
+    ref = make_golden.live_checks()[0]["reference_parse_cfg"]
+    paths = dict(zip(("darknet_dynamic.cfg", "reweighting_net.cfg", "tiny-yolo-voc.cfg"), cfgs.write_standard_cfgs(str(tmp_path))))
+    paths["yolo-voc.cfg"] = make_golden.write_cfg_blocks(ref["yolo-voc.cfg"], str(tmp_path / "yolo-voc.cfg"))
+    assert sorted(paths) == sorted(ref)
+    for name, p in paths.items():
+        assert parse_cfg(p) == ref[name], name
 
 
-@needs_ref
-def test_full_size_construction_matches_live_reference():
-    ref = ref_shim.load("darknet_meta")
-    d = os.path.join(ref_shim.REF, "cfg")
-    r = ref.Darknet(os.path.join(d, "darknet_dynamic.cfg"), os.path.join(d, "reweighting_net.cfg"))
-    o = OracleDarknet(os.path.join(d, "darknet_dynamic.cfg"), os.path.join(d, "reweighting_net.cfg"))
-    rs, os_ = r.state_dict(), o.state_dict()
-    assert list(rs.keys()) == list(os_.keys())
-    assert all(rs[k].shape == os_[k].shape for k in rs)
+def test_full_size_construction_matches_live_reference(tmp_path):
+    """The full-size oracle model has the reference Darknet's state_dict: same keys in the same order, same shapes
+    (the reference's: tests/golden/live_checks.json)."""
+    from fewshot_detection_amd import cfgs
+    ref = make_golden.live_checks()[0]["state_dict_shapes"]
+    dyn, rw, _ = cfgs.write_standard_cfgs(str(tmp_path))
+    o = OracleDarknet(dyn, rw)
+    os_ = o.state_dict()
+    assert list(os_.keys()) == [k for k, _ in ref]
+    assert all(list(os_[k].shape) == shape for k, shape in ref)
     assert sum(p.numel() for p in o.parameters()) == 66287742
 
 
@@ -185,43 +189,41 @@ def _nasty_targets(rng, bs, cs, grid):
     return tgt
 
 
-@pytest.mark.parametrize("seed", range(16))
-def test_region_loss_v2_live_sweep(seed):
-    """The oracle against the LIVE reference RegionLossV2 (py2->py3 shim) on randomised nasty targets: every mask of
-    build_targets bit-exact, loss and gradient equal.  Skipped where /root/reference is absent (GPU box)."""
-    import random
-    import ref_shim
-    if not ref_shim.available():
-        pytest.skip("reference tree not present")
-    import make_golden
-    from oracle.region import region_loss_v2
-    cfgmod, rl = ref_shim.load("cfg"), ref_shim.load("region_loss")
+def _sweep_case(seed):
+    """Inputs of one case of the RegionLossV2 sweep -> (output, target, seen, neg_ratio, reason the reference cannot run it)."""
     rng = np.random.RandomState(500 + seed)
     bs, cs, grid = int(rng.randint(1, 4)), int(rng.choice([1, 3, 5])), int(rng.choice([5, 7, 13]))
     seen = int(rng.choice([0, 12800, 20000]))
     neg = ["full", 0, 1][seed % 3]
     tgt = _nasty_targets(rng, bs, cs, grid)
     out = torch.from_numpy(rng.randn(bs * cs, 30, grid, grid).astype(np.float32) * 1.5)
-    mod = rl.RegionLossV2()
-    mod.anchors, mod.num_anchors, mod.num_classes, mod.anchor_step = make_golden.ANCH, 5, 1, 2
-    mod.seen = seen
-    cfgmod.cfg.neg_ratio = neg
-    try:
-        if not (tgt.reshape(bs * cs, -1).sum(1) != 0).any() and neg != "full":
-            pytest.skip("no positive row: the reference divides by zero here")
-        n_pos = int((tgt.reshape(bs * cs, -1).sum(1) != 0).sum())
-        if neg == 0 and n_pos == 1:
-            # reference quirk (SURVEY 8a'): np.argwhere(flags).squeeze() is 0-d for a single surviving row, pred[inds]
-            # loses its batch dimension and the reference raises a shape error; the oracle / kernels keep the row
-            pytest.skip("single surviving row: the reference itself raises here")
-        random.seed(seed)
-        ref = make_golden._run_loss(rl, mod, out, torch.from_numpy(tgt))
-        random.seed(seed)
-        o = out.clone().requires_grad_(True)
-        r = region_loss_v2(o, torch.from_numpy(tgt), make_golden.ANCH, seen=seen, neg_ratio=neg)
-        r["loss"].backward()
-    finally:
-        cfgmod.cfg.neg_ratio = "full"
+    skip = None
+    if not (tgt.reshape(bs * cs, -1).sum(1) != 0).any() and neg != "full":
+        skip = "no positive row: the reference divides by zero here"
+    elif neg == 0 and int((tgt.reshape(bs * cs, -1).sum(1) != 0).sum()) == 1:
+        # reference quirk (SURVEY 8a'): np.argwhere(flags).squeeze() is 0-d for a single surviving row, pred[inds]
+        # loses its batch dimension and the reference raises a shape error; the oracle / kernels keep the row
+        skip = "single surviving row: the reference itself raises here"
+    return out, tgt, seen, neg, skip
+
+
+@pytest.mark.parametrize("seed", range(16))
+def test_region_loss_v2_live_sweep(seed):
+    """The oracle against the reference RegionLossV2 on randomised nasty targets: every mask of build_targets bit-exact,
+    loss and gradient equal.  The reference's results are in tests/golden/live_checks.npz (make_golden.py runs the
+    reference through the py2->py3 shim on these very inputs)."""
+    import random
+    from oracle.region import region_loss_v2
+    out, tgt, seen, neg, skip = _sweep_case(seed)
+    if skip:
+        pytest.skip(skip)
+    ref = make_golden.live_checks()[1]
+    ref = {k: ref["sweep%d_%s" % (seed, k)] for k in ("nGT", "nCorrect", "coord_mask", "conf_mask", "cls_mask", "tx", "ty", "tw",
+                                                      "th", "tconf", "tcls", "loss", "grad")}
+    random.seed(seed)
+    o = out.clone().requires_grad_(True)
+    r = region_loss_v2(o, torch.from_numpy(tgt), make_golden.ANCH, seen=seen, neg_ratio=neg)
+    r["loss"].backward()
     assert (r["nGT"], r["nCorrect"]) == (int(ref["nGT"]), int(ref["nCorrect"]))
     for k in ("coord_mask", "conf_mask", "cls_mask", "tx", "ty", "tw", "th", "tconf", "tcls"):
         assert np.array_equal(r["targets"][k], ref[k]), k
@@ -229,11 +231,11 @@ def test_region_loss_v2_live_sweep(seed):
     assert np.allclose(o.grad.numpy(), ref["grad"], rtol=1e-5, atol=1e-6)
 
 
-@needs_ref
 def test_global_pools_match_live_reference_pooling():
-    """pooling.py:8-45: the oracle's [globalmax] / [globalavg] layers are the reference's GlobalMaxPool2d / GlobalAvgPool2d."""
+    """pooling.py:8-45: the oracle's [globalmax] / [globalavg] layers are the reference's GlobalMaxPool2d / GlobalAvgPool2d
+    (their outputs on this input: tests/golden/live_checks.npz)."""
     from oracle.net import _GlobalAvg, _GlobalMax
-    ref = ref_shim.load("pooling")
+    ref = make_golden.live_checks()[1]
     x = torch.randn(3, 16, 6, 6, generator=torch.Generator().manual_seed(3))
-    assert torch.equal(_GlobalMax()(x), ref.GlobalMaxPool2d()(x))
-    assert torch.equal(_GlobalAvg()(x), ref.GlobalAvgPool2d()(x))
+    assert torch.equal(_GlobalMax()(x), torch.from_numpy(ref["pool_max"]))
+    assert torch.equal(_GlobalAvg()(x), torch.from_numpy(ref["pool_avg"]))

@@ -7,7 +7,7 @@ R="$GRAFT_REPO_ROOT"; O="$R/gpurun_out/r06z"; rm -rf "$O"; mkdir -p "$O"; export
 export TMPDIR=/tmp; cd "$R"
 ( timeout 600 python tools/alloc_trace.py ) > "$O/alloc_trace_f32.txt" 2> "$O/alloc_trace_f32.err"; echo "alloc trace f32 rc=$?"; head -3 "$O/alloc_trace_f32.txt" | cut -c1-250
 ( timeout 600 python tools/alloc_trace.py --dtype bf16 ) > "$O/alloc_trace_bf16.txt" 2> "$O/alloc_trace_bf16.err"; echo "alloc trace bf16 rc=$?"; head -3 "$O/alloc_trace_bf16.txt" | cut -c1-250
-( time timeout 900 python bench.py --steps 20 --warmup 5 ) > "$O/bench_f32.json" 2> "$O/bench_f32.err"; echo "bench f32 rc=$?"
+( time timeout 900 python bench.py --steps 20 --warmup 5 --full ) > "$O/bench_f32.json" 2> "$O/bench_f32.err"; echo "bench f32 rc=$?"
 cp gpurun_out/bench_full_f32_n1.json "$O/bench_full_f32.json" 2>/dev/null
 ( time timeout 600 python bench.py --classes 15 --support 416 --no-cpu-baseline --no-extras ) > "$O/bench_c2cfg.json" 2> "$O/bench_c2cfg.err"; echo "bench c2 rc=$?"
 cd /tmp
